@@ -14,6 +14,8 @@ every rank decrypts its own `--batch`); RCCL carries the barrier, the MAX-over-r
 config -- the one real exchange of the domain: the all-gather of the partial decryptions before the local combine.
 
 Prints ONE JSON line on rank 0.
+`--dump-outputs DIR` also writes what the headline's last timed step returned on rank 0 (decrypt_plaintext.npy, see
+dump_outputs); the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -199,6 +201,25 @@ def host_cpu_info():
     return info
 
 
+DUMP_BYTES_MAX = 64 * 10**6
+
+
+def dump_outputs(out_dir: str, plain) -> None:
+    """Writes the plaintexts of the headline's last timed step as DIR/decrypt_plaintext.npy: one row per ciphertext, its
+    big-endian bytes as 16-bit digits in float32 (exact).  A batch whose rows exceed DUMP_BYTES_MAX is cut to a fixed
+    sample of rows (seed 0, ascending); DIR/decrypt_rows.npy (float64) says which rows were written."""
+    import numpy as np
+    rows, nbytes = plain.shape
+    if nbytes % 2:
+        plain = np.pad(plain, ((0, 0), (1, 0)))
+    digits = (plain[:, 0::2].astype(np.uint32) << 8 | plain[:, 1::2]).astype(np.float32)
+    keep = min(rows, DUMP_BYTES_MAX // (digits.shape[1] * 4 + 8))
+    idx = np.arange(rows) if keep == rows else np.sort(np.random.default_rng(0).choice(rows, keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "decrypt_plaintext.npy"), np.ascontiguousarray(digits[idx]))
+    np.save(os.path.join(out_dir, "decrypt_rows.npy"), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -218,7 +239,11 @@ def main():
     ap.add_argument("--rehearse-one-gpu", action="store_true",
                     help="N > 1 ranks that all use GPU 0 and exchange over gloo: rehearses the multi-rank code path (self-launch, "
                          "sharding, the threshold exchange, the reductions) on a one-GPU box; not a measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's last step returned (rank 0's plaintexts) to DIR as .npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.headline_only:
         args.no_cpu_baseline = args.no_extra = args.no_traffic = True
 
@@ -350,6 +375,8 @@ def main():
     if not ok:
         bad = int((out_dev != m_dev).any(dim=1).sum().item())
         raise SystemExit(f"[bench] rank {rank}: PARITY FAILURE: {bad} of {B} decryptions differ from the plaintexts")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out_dev.cpu().numpy())
 
     # ---- extra configs (BASELINE.json configs 2-5), same process, same rules: inputs resident in HBM, HIP-event kernel
     # time, executed multiply-adds from the library's per-opcode count, full-batch round-trip parity where one exists ------
